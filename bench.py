@@ -9,6 +9,7 @@ pairs per GPU at 16 x 224^2 frames / 32 tokens (BASELINE.json configs[2]; `--wor
 bf16 storage / fp32 accumulation, weights cast from the fp32 masters inside every timed step, data-parallel gradient all-reduce (flat per-block buffers, or DDP)
 over RCCL for N > 1.  Prints ONE JSON line (rank 0) with the contract fields + `roofline` (dominant kernel: the MFMA GEMM,
 timed with HIP events on its own stream inside the timed region) + `cpu_baseline` (the CPU oracle timed on the host cores).
+`--dump-outputs DIR` also writes what the last timed step computed (losses, sampled gradients) as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import json
@@ -147,6 +148,35 @@ def cpu_baseline(cfg, L, workload, timeout_s=330, budget_s=240):
             "flops_ratio_workload_over_sample": round(ratio, 3)}
 
 
+DUMP_BUDGET_BYTES = 60 << 20    # --dump-outputs: array payload; with the .npy headers the directory stays under 64 MB
+
+
+def dump_outputs(out_dir, losses, model, with_params):
+    """Write what one timed step hands its caller: the loss dict (float64 scalars, `<key>.npy`), every parameter gradient
+    (`grad.<name>.npy`) and, when the step includes the optimizer, every updated parameter (`param.<name>.npy`).  A tensor larger
+    than the per-tensor share of DUMP_BUDGET_BYTES is written as a sample at sorted indices drawn from a generator seeded by the
+    tensor's name and size, so that the same arguments select the same elements in every run and every build.  Gradients that
+    the step left as None are not written."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in losses.items():
+        np.save(os.path.join(out_dir, f'{k}.npy'), np.asarray(float(v.detach()), dtype=np.float64))
+    named = list(model.named_parameters())
+    sets = [('grad', lambda p: p.grad)] + ([('param', lambda p: p)] if with_params else [])
+    per_tensor = DUMP_BUDGET_BYTES // 4 // (len(sets) * len(named))
+    for prefix, get in sets:
+        for name, p in named:
+            t = get(p)
+            if t is None:
+                continue
+            flat = t.detach().reshape(-1)
+            if flat.numel() > per_tensor:
+                g = torch.Generator().manual_seed(zlib.crc32(f'{name}:{flat.numel()}'.encode()))
+                idx = torch.randint(0, flat.numel(), (per_tensor,), generator=g).sort().values
+                flat = flat[idx.to(flat.device)]
+            np.save(os.path.join(out_dir, f'{prefix}.{name}.npy'), flat.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -173,7 +203,12 @@ def main():
     ap.add_argument('--grad-wire', default=None, choices=['fp32', 'bf16'],
                     help='--grad-sync flat: fp32 = in-place all-reduce (default), bf16 = bf16 on the links with fp32 accumulation on arrival '
                          '(grad_sync.allreduce_bf16_wire; half the bytes, two bf16 roundings per gradient element)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed to DIR/<name>.npy (rank 0): every loss '
+                         '(float64), a fixed seeded sample of every parameter gradient and, with --optimizer, of every updated '
+                         'parameter (float32); at most 64 MB in all (see dump_outputs)')
     a = ap.parse_args()
+    assert a.steps >= 1, "--steps must be >= 1"
 
     import torch.distributed as dist
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -271,6 +306,8 @@ def main():
     sync()
     dt = time.perf_counter() - t0
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps))
+    if a.dump_outputs and rank == 0:                # before the event passes below run more steps over these gradients
+        dump_outputs(a.dump_outputs, ld, model, optimizer is not None)
     # Per-kernel durations for the roofline object: the same K steps twice more with one HIP event pair around every GEMM,
     # attention and LayerNorm launch, on the stream the kernel is launched on -- once exactly as timed above (text-side and
     # weight-gradient kernels share the CUs with the kernel being timed: "in_step", what rocprofv3 sees in the step) and once
