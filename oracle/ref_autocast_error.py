@@ -1,6 +1,8 @@
 """How far is the REFERENCE ITSELF from its fp32 values when it runs the way its trainer runs it -- under autocast
-(trainer_egoclip.py:143; bf16 here, CPU autocast: matmuls / convolutions in bf16, LayerNorm, softmax, residual sums and losses
-in fp32)?  Puts the bf16 mode of this build (activations stored in bf16) in context.  Build container only
+(trainer_egoclip.py:143; bf16 here, CPU autocast: matmuls / convolutions in bf16; every other op in its inputs' dtype -- unlike CUDA
+autocast, CPU autocast (torch 2.10) returns softmax and layer_norm in bf16 for a bf16 input, so the attention probabilities are
+rounded to bf16 here, and a residual sum is fp32 only when one operand is; tests/test_block_parity.py's _Mixed is the CUDA policy)?
+Puts the bf16 mode of this build (activations stored in bf16) in context.  Build container only
 (imports /root/reference through oracle/gen_golden.py).  usage: python oracle/ref_autocast_error.py [base_f4|base_f16|tiny] [--grads] [--write]"""
 import os, sys, types
 import numpy as np
