@@ -17,7 +17,7 @@ from . import switches as _sw  # noqa: E402
 
 LIB_PATH = _sw.value('EGV_LIB_PATH') or os.path.join(_HERE, 'libegovlp_hip.so')
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 EGV_F32, EGV_BF16 = 0, 1
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_TANH, ACT_GELU_D = 0, 1, 2, 3, 4
 
@@ -62,6 +62,7 @@ class VBlockDesc(C.Structure):
         ('next_g', vp), ('next_b', vp), ('next_h', vp), ('next_stats', vp),
         ('fwd_cus', i32),
         ('acc_mask', C.c_uint),
+        ('dp_scale', vp * 2),
     ]
 
 
@@ -164,6 +165,7 @@ PROTOTYPES = {
     'egv_egonce_fwd': (i32, [vp, vp, vp, i32, f32, i32, i32, vp, vp, vp, vp]),
     'egv_egonce_bwd': (i32, [vp, vp, vp, vp, vp, vp, i32, f32, i32, i32, vp]),
     'egv_adamw_step': (i32, [vp, vp, i32, i32, f32, f32, f32, f32, f32, f32, f32, vp]),
+    'egv_drop_path_scales': (i32, [i32, f32, C.c_uint, vp, vp]),
     'egv_vblock_qkv_s_offset': (i64, [C.POINTER(VBlockDesc)]),
     'egv_vblock_next_slots': (i32, [C.POINTER(VBlockDesc), C.POINTER(i64), C.POINTER(i64)]),
     'egv_vblock_save_bytes': (i64, [C.POINTER(VBlockDesc)]),

@@ -23,6 +23,11 @@ void egv_gemm_set_cu_limit(int n);                  // egv_gemm3.hip: CUs the pe
 void egv_gemm_set_cu_slack(int n);                  // ... and how many CUs beyond that plan a grid may take to save a round (-1: EGV_PP_LIMIT_SLACK)
 void egv_ln_bwd_defer_begin(void* ws, long long bytes);     // egv_norm.hip: the LayerNorm parameter-gradient partials of a call summed by ONE launch
 int egv_ln_bwd_defer_flush(void* stream);
+void egv_gemm_set_row_scale(const float* s, int rows_per_group);     // egv_gemm.hip: per-row-group gate of this thread's egv_gemm calls
+int egv_sum_layernorm_dp(const float* base32, const void* base16, const void* d1, const void* d2, const void* dg, const float* gate,
+                         float* sum32, void* sum16, void* y, const float* gamma, const float* beta, float* stats, int M, int D,
+                         float eps, const float* m1, const float* m2, int S, void* stream);     // egv_norm.hip
+int egv_scale_rows(int dtype, const void* x, const float* m, void* y, int M, int D, int S, void* stream);   // egv_misc.hip
 extern "C" int egv_layernorm_bwd2(int dtype, const void* dy, const void* x, const float* stats, const float* gamma,
                                   const void* add, const void* add2, void* dx, float* dgamma, float* dbeta, int M, int D,
                                   void* workspace, void* stream);
@@ -408,6 +413,19 @@ bool vdefer_ok(const egv_vblock_desc* d) {
     const int ntile = 2 * tD * tH + 2 * tD * tD + 2 * 3 * tD * tD + (d->L > 0 ? 2 * tD * tD : 0);
     return vfp8_on(d) || ntile <= max_tiles;
 }
+// Stochastic depth (egv_vblock_desc::dp_scale): the forms that take it are the unfused block in fp32, in bf16 with the bf16 stream and
+// in bf16 with the fp32 stream (EGV_BLOCK_RES_F32); the fused form, MX-fp8 operands and the CLS-only head call refuse it
+int vdp_check(const egv_vblock_desc* d, const char* who) {
+    if (!d->dp_scale[0] && !d->dp_scale[1]) return 0;
+    const char* why = d->L > 0 ? "the fused form (L > 0)" : (d->flags & EGV_BLOCK_FP8) ? "EGV_BLOCK_FP8" : (d->flags & EGV_BLOCK_HEAD) ? "EGV_BLOCK_HEAD" : nullptr;
+    if (why) { egv_set_error("%s: drop path (dp_scale) is not supported with %s", who, why); return -1; }
+    return 0;
+}
+struct RowScale {                                   // scoped egv_gemm_set_row_scale (NULL: nothing set)
+    bool on;
+    RowScale(const float* s, int rows) : on(s != nullptr) { if (on) egv_gemm_set_row_scale(s, rows); }
+    ~RowScale() { if (on) egv_gemm_set_row_scale(nullptr, 1); }
+};
 struct CuLimit {                                    // scoped egv_gemm_set_cu_limit / egv_gemm_set_cu_slack
     bool on;
     explicit CuLimit(int n, int slack = -1) : on(n > 0) { if (on) { egv_gemm_set_cu_limit(n); egv_gemm_set_cu_slack(slack); } }
@@ -469,6 +487,8 @@ extern "C" long long egv_vblock_ws_bytes(const egv_vblock_desc* d, int backward)
         mx(vgroup_ws_bytes(d));
         tot += al((size_t)wg) + al((size_t)egv_layernorm_bwd_workspace_bytes((int)M, (int)D)) + al(ln_defer_bytes((int)M, (int)D));
         tot += al(M * Hd * es) + 8 * al(M * D * es) + 2 * al(M * 3 * D * es) + 3 * al(M * H * 4) + 4096;
+        for (int i = 0; i < 2; ++i)
+            if (d->dp_scale[i]) tot += al(M * D * es);                                  // the scaled gradient entering a dropped-path branch
         if (d->L > 0) tot += 4 * al(M * D * es) + al((size_t)d->B * d->L * 2 * D * es) + 4096;
     }
     return (long long)tot + 65536;
@@ -481,6 +501,9 @@ extern "C" int egv_vblock_fwd(const egv_vblock_desc* d) {
     const bool head = (d->flags & EGV_BLOCK_HEAD) != 0;             // stop after the space attention's qkv projection (its slot of `save` is the result)
     if (!(d->x && (d->out || head) && d->save && d->ws)) { egv_set_error("egv_vblock_fwd: null buffer"); return -1; }
     if (head && !(d->flags & EGV_BLOCK_RES_F32)) { egv_set_error("egv_vblock_fwd: EGV_BLOCK_HEAD is built for the fp32 residual stream form"); return -1; }
+    BCHK(vdp_check(d, "egv_vblock_fwd"));
+    const float* const dpa = d->dp_scale[0];                        // stochastic depth: space branch, MLP branch (NULL: not scaled)
+    const float* const dpm = d->dp_scale[1];
     const VLayout L = vlayout(d);
     if ((long long)L.total > d->save_bytes) { egv_set_error("egv_vblock_fwd: save buffer too small"); return -1; }
     char* sv = (char*)d->save;
@@ -539,9 +562,10 @@ extern "C" int egv_vblock_fwd(const egv_vblock_desc* d) {
         void* ys = ws.take((size_t)M * D * esz(dt));
         if (!ws.ok()) { egv_set_error("egv_vblock_fwd: workspace too small"); return -1; }
         const float* x32 = d->x32;
-        auto sumln = [&](const void* d1, const void* d2, const void* dg, float* s32, void* s16, void* y, int ln, float* stats) -> int {
-            return egv_sum_layernorm(x32, x32 ? nullptr : d->x, d1, d2, dg, dg ? d->alpha : nullptr, s32, s16, y, y ? d->ln_g[ln] : nullptr,
-                                     y ? d->ln_b[ln] : nullptr, stats, M, D, d->eps, st);
+        auto sumln = [&](const void* d1, const void* d2, const void* dg, float* s32, void* s16, void* y, int ln, float* stats,
+                         const float* m1 = nullptr) -> int {
+            return egv_sum_layernorm_dp(x32, x32 ? nullptr : d->x, d1, d2, dg, dg ? d->alpha : nullptr, s32, s16, y, y ? d->ln_g[ln] : nullptr,
+                                        y ? d->ln_b[ln] : nullptr, stats, M, D, d->eps, m1, nullptr, S, st);
         };
         if (!(d->flags & EGV_BLOCK_H3_READY))                     // (else the previous block's output pass left norm3(x) and its statistics in place)
             BCHK(sumln(nullptr, nullptr, nullptr, nullptr, nullptr, sv + L.h3, VL_NORM3, (float*)(sv + L.stats3)));
@@ -567,13 +591,14 @@ extern "C" int egv_vblock_fwd(const egv_vblock_desc* d) {
             BCHK(lin_fwd(dt, M, D, D, sv + L.o, d->w[VW_PROJ_I2T], d->b[VW_PROJ_I2T], sv + L.pg, 0, nullptr, nullptr, nullptr, nullptr, st));
             a1 = sv + L.s; ag = sv + L.pg;
         }
-        BCHK(sumln(a1, nullptr, ag, nullptr, lean ? nullptr : sv + L.sr, sv + L.h2, VL_NORM2, (float*)(sv + L.stats2)));
+        BCHK(sumln(a1, nullptr, ag, nullptr, lean ? nullptr : sv + L.sr, sv + L.h2, VL_NORM2, (float*)(sv + L.stats2), dpa));   // sr = x + m_attn * a1
         BCHK(lin(VW_FC1, Hd, D, sv + L.h2, sv + L.act, mlp_act(dt), nullptr, fc1_pre));
         BCHK(lin(VW_FC2, D, Hd, sv + L.act, d->out, 0, nullptr, nullptr));                         // the MLP's output, then out = sr + it in place
         // the block's output sum, in fp32 and bf16 -- and, when the caller names the next block's norm3 and save slots, that LayerNorm too
+        // (drop path: out = x + m_attn * a1 + m_mlp * fc2(..), the sr of the call above plus the scaled MLP branch)
         const bool fold = d->next_h && d->next_g && d->next_b && d->next_stats;
-        return egv_sum_layernorm(x32, x32 ? nullptr : d->x, a1, d->out, ag, ag ? d->alpha : nullptr, d->out32, d->out, fold ? d->next_h : nullptr,
-                                 fold ? d->next_g : nullptr, fold ? d->next_b : nullptr, fold ? d->next_stats : nullptr, M, D, d->eps, st);
+        return egv_sum_layernorm_dp(x32, x32 ? nullptr : d->x, a1, d->out, ag, ag ? d->alpha : nullptr, d->out32, d->out, fold ? d->next_h : nullptr,
+                                    fold ? d->next_g : nullptr, fold ? d->next_b : nullptr, fold ? d->next_stats : nullptr, M, D, d->eps, dpa, dpm, S, st);
     }
     // temporal attention (video_transformer.py:217-218): x + proj(attn(qkv(norm3 x)))
     BCHK(ln_lin(VL_NORM3, d->x, sv + L.h3, (float*)(sv + L.stats3), VW_TQKV, 3 * D, D, sv + L.qkv_t, 0, nullptr));
@@ -583,6 +608,7 @@ extern "C" int egv_vblock_fwd(const egv_vblock_desc* d) {
     BCHK(ln_lin(VL_NORM1, sv + L.tr, sv + L.h1, (float*)(sv + L.stats1), VW_SQKV, 3 * D, D, sv + L.qkv_s, 0, nullptr));
     BCHK(dvs.fwd(sv + L.qkv_s, sv + L.sctx, (float*)(sv + L.lse_s), aws, awb, st));
     if (!fused) {
+        RowScale rs(dpa, S);                                                                       // sr = x + m_attn[row / S] * proj(..)
         BCHK(lin(VW_SPROJ, D, D, sv + L.sctx, sv + L.sr, 0, d->x, nullptr));
     } else {
         // image-to-text cross attention (:155-185): s = proj(ctx); q from norm_i2t_i(s), k|v from the text states; x + s + alpha*proj_i2t(o)
@@ -596,7 +622,10 @@ extern "C" int egv_vblock_fwd(const egv_vblock_desc* d) {
     // MLP (:226): sr + fc2(gelu(fc1(norm2 sr)))
     BCHK(ln_lin(VL_NORM2, sv + L.sr, sv + L.h2, (float*)(sv + L.stats2), VW_FC1, Hd, D, sv + L.act, mlp_act(dt), fc1_pre));
     if (mlp_chain) BCHK(f8.lin_from_q2(D, Hd, d->wq[VW_FC2], d->wq_s[VW_FC2], d->b[VW_FC2], d->out, sv + L.sr));
-    else BCHK(lin(VW_FC2, D, Hd, sv + L.act, d->out, 0, sv + L.sr, nullptr));
+    else {
+        RowScale rs(dpm, S);                                                                       // out = sr + m_mlp[row / S] * fc2(..)
+        BCHK(lin(VW_FC2, D, Hd, sv + L.act, d->out, 0, sv + L.sr, nullptr));
+    }
     return 0;
 }
 
@@ -624,6 +653,9 @@ extern "C" int egv_vblock_bwd(const egv_vblock_desc* d) {
     const bool fused = d->L > 0;
     if (!(d->x && d->dout && d->dx && d->save && d->ws)) { egv_set_error("egv_vblock_bwd: null buffer"); return -1; }
     const bool head = (d->flags & EGV_BLOCK_HEAD) != 0;             // dout = the gradient of the space attention's qkv [M, 3D]; the call starts there
+    BCHK(vdp_check(d, "egv_vblock_bwd"));
+    const float* const dpa = d->dp_scale[0];
+    const float* const dpm = d->dp_scale[1];
     const VLayout L = vlayout(d);
     const char* sv = (const char*)d->save;
     void* st = d->stream;
@@ -676,6 +708,10 @@ extern "C" int egv_vblock_bwd(const egv_vblock_desc* d) {
         f8.q2 = ws.take((size_t)M * Hd);
         f8.s2 = ws.take((size_t)egv_mx_scale_bytes(M, Hd, 0));
     }
+    // drop path: the gradients entering the space / MLP branch, m[row / S] * (d_sr | dout), once each -- the operand of the branch's
+    // weight / bias gradients (a reduction over the rows) and of its data gradient (exact zeros for a dropped sample)
+    void* const d_sr_m = dpa ? ws.take((size_t)M * D * es) : nullptr;
+    void* const dout_m = dpm ? ws.take((size_t)M * D * es) : nullptr;
     if (!ws.ok()) { egv_set_error("egv_vblock_bwd: workspace too small (%zu > %zu)", ws.off, ws.cap); return -1; }
     static const bool epi_q = egv_cfg_on("EGV_MX_EPI_QUANT", true);
     const bool mlp_chain = epi_q && f8.on && d->wtq[VW_FC1] && d->wtq_s[VW_FC1] && d->wtq[VW_FC2] && d->wtq_s[VW_FC2];
@@ -715,16 +751,21 @@ extern "C" int egv_vblock_bwd(const egv_vblock_desc* d) {
     };
 
     if (!head) {
-    // ---- MLP: out = sr + fc2(gelu(pre)), pre = fc1(h2)
-    BCHK(wgrad(D, Hd, d->dout, sv + L.act, VW_FC2, nullptr, M));
+    // ---- MLP: out = sr + fc2(gelu(pre)), pre = fc1(h2)  (drop path: out = sr + m_mlp * fc2(..), the branch sees m_mlp * dout)
+    const void* dmlp = d->dout;
+    if (dpm) {
+        BCHK(egv_scale_rows(dt, d->dout, dpm, dout_m, M, D, S, st));
+        dmlp = dout_m;
+    }
+    BCHK(wgrad(D, Hd, dmlp, sv + L.act, VW_FC2, nullptr, M));
     if (mlp_chain) {
         // fc2's data gradient writes dpre = (dout W2) * gelu'(pre) in bf16 (the weight gradient of fc1 reads it) AND in MX-fp8 form:
         // the operand of fc1's data gradient, without a quantiser launch
-        BCHK(f8.lin_qout(Hd, D, d->dout, false, d->wtq[VW_FC2], d->wtq_s[VW_FC2], nullptr, dpre, 0, nullptr, sv + L.pre, mlp_act(dt)));
+        BCHK(f8.lin_qout(Hd, D, dmlp, false, d->wtq[VW_FC2], d->wtq_s[VW_FC2], nullptr, dpre, 0, nullptr, sv + L.pre, mlp_act(dt)));
         BCHK(wgrad(Hd, D, dpre, sv + L.h2, VW_FC1, nullptr, M));
         BCHK(f8.lin_from_q2(D, Hd, d->wtq[VW_FC1], d->wtq_s[VW_FC1], nullptr, dh2, nullptr));
     } else {
-        BCHK(dgrad(VW_FC2, D, Hd, d->dout, dpre, sv + L.pre, mlp_act(dt)));
+        BCHK(dgrad(VW_FC2, D, Hd, dmlp, dpre, sv + L.pre, mlp_act(dt)));
         BCHK(wgrad(Hd, D, dpre, sv + L.h2, VW_FC1, nullptr, M));
         BCHK(dgrad(VW_FC1, Hd, D, dpre, dh2, nullptr, 0));
     }
@@ -732,6 +773,10 @@ extern "C" int egv_vblock_bwd(const egv_vblock_desc* d) {
     BCHK(egv_layernorm_bwd2(dt, dh2, sv + L.sr, (const float*)(sv + L.stats2), d->ln_g[VL_NORM2], d->dout, nullptr, d_sr, d->dln_g[VL_NORM2],
                             d->dln_b[VL_NORM2], M, D, lnw, st));
     const void* d_sproj_out = d_sr;                          // gradient at the output of attn.proj
+    if (dpa) {                                               // drop path: sr = x + m_attn * proj(..) -- the skip keeps d_sr, the branch gets m_attn * d_sr
+        BCHK(egv_scale_rows(dt, d_sr, dpa, d_sr_m, M, D, S, st));
+        d_sproj_out = d_sr_m;
+    }
     if (fused) {
         // sr = alpha * P + s + x, P = proj_i2t(o) (saved as pg)
         const int BL = d->B * d->L;

@@ -17,6 +17,11 @@ struct GemmEpi {
     float scale;         // host scalar applied to the accumulator first
     unsigned char* oq = nullptr;   // MX-fp8 form only: the output also as e4m3 codes [M][N] ...
     unsigned char* os = nullptr;   // ... and role-0 scale bytes (egv_mx.hip)
+    // per-row-group gate (stochastic depth, video_transformer.py:222,226): v *= rscale[m / rgroup] after the scalar gate, before the
+    // residual adds -- row m of the flat [B*S, D] token matrix belongs to sample m / S.  Taken by the generic and the ring kernels;
+    // the persistent kernel declines such a call (egv_gemm3_launch).  nullptr: no row scale (the kernels' code paths as before).
+    const float* rscale = nullptr;
+    int rgroup = 1;
 };
 
 struct GemmArgs {
@@ -92,6 +97,11 @@ __device__ __forceinline__ void gemm_epilogue4(const GemmArgs& g, OutT* C, int m
     if (e.gate) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) { v[r] *= gate; asm volatile("" : "+v"(v[r])); }   // product rounded on its own in every GEMM kernel: never contracted with the residual add
+    }
+    if (e.rscale) {
+        const float rs = e.rscale[m / e.rgroup];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { v[r] *= rs; asm volatile("" : "+v"(v[r])); }        // (as the gate: rounded on its own)
     }
     if (R1) {
         float x[4] = {0.f, 0.f, 0.f, 0.f};

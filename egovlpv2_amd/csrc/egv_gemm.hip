@@ -342,6 +342,15 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const bf16_t* __restri
     }
 }
 
+// per-row-group gate of the next egv_gemm calls of this thread (GemmEpi::rscale): the block executor's stochastic depth
+// (egv_block.cpp sets it around the attn.proj / mlp.fc2 forward GEMMs of a call with egv_vblock_desc::dp_scale and clears it)
+static thread_local const float* t_row_scale = nullptr;
+static thread_local int t_row_group = 1;
+void egv_gemm_set_row_scale(const float* s, int rows_per_group) {
+    t_row_scale = s;
+    t_row_group = rows_per_group > 0 ? rows_per_group : 1;
+}
+
 extern "C" int egv_gemm(int dtype, int a_trans, int b_trans, int M, int N, int K,
                         const void* A, int lda, const void* B, int ldb, void* C, int ldc, int out_f32,
                         const float* bias, int act, const float* gate, const void* res1, const void* res2,
@@ -363,13 +372,14 @@ extern "C" int egv_gemm(int dtype, int a_trans, int b_trans, int M, int N, int K
     g.tiles_n = (N + BN - 1) / BN;
     g.e.bias = bias; g.e.gate = gate; g.e.res1 = res1; g.e.res2 = res2; g.e.pre = pre; g.e.aux = aux;
     g.e.act = act; g.e.dact = dact; g.e.ldr = ldr ? ldr : ldc; g.e.scale = scale;
+    g.e.rscale = t_row_scale; g.e.rgroup = t_row_group;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const double es_ = dtype == EGV_BF16 ? 2.0 : 4.0;
     // algorithmic bytes: operands + output once, plus every epilogue operand that is read or written
     const double abytes = es_ * ((double)M * K + (double)N * K + (double)M * N * (1 + (res1 != nullptr) + (res2 != nullptr) + (pre != nullptr) + (aux != nullptr)));
     void* ph = egv_prof_begin(stream);
     if (dtype == EGV_BF16 && !a_trans && !b_trans && !out_f32 && M <= 16 && N >= 512 && K >= 512 && (K % 8) == 0 && g.a_vec_ok && g.b_vec_ok &&
-        !gate && !res1 && !res2 && !aux && !dact && scale == 1.0f && (act == 0 || act == 1 || act == 2 || act == 3) && (!pre || (act == 1 && g.e.ldr == ldc))) {
+        !gate && !t_row_scale && !res1 && !res2 && !aux && !dact && scale == 1.0f && (act == 0 || act == 1 || act == 2 || act == 3) && (!pre || (act == 1 && g.e.ldr == ldc))) {
         hipLaunchKernelGGL(gemm_skinny_kernel, dim3((N + 15) / 16), dim3(256), 0, st, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, (bf16_t*)C, ldc,
                            bias, act, M, N, K, (bf16_t*)pre);
         egv_prof_end(ph, stream, 2.0 * M * N * K, 7, abytes);        // 7 = skinny (<= 16 rows)

@@ -177,6 +177,11 @@ __global__ __launch_bounds__(512) void gemm_ring_kernel(const GemmArgs g) {
 #pragma unroll
                     for (int k = 0; k < 8; ++k) { v[k] *= gate; asm volatile("" : "+v"(v[k])); }   // not contracted with the residual add (bit-equal across the GEMM kernels)
                 }
+                if (e.rscale) {                                    // per-sample stochastic-depth multiplier (GemmEpi::rscale)
+                    const float rs = e.rscale[m / e.rgroup];
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) { v[k] *= rs; asm volatile("" : "+v"(v[k])); }
+                }
                 if (R1) {
                     const u32x4_t r = *reinterpret_cast<const u32x4_t*>(R1 + ro);
 #pragma unroll

@@ -858,6 +858,7 @@ int egv_gemm3_launch(const GemmArgs& gin, hipStream_t st) {
     if ((long long)g.M * g.ldc >= (1LL << 30) || (long long)g.M * e.ldr >= (1LL << 30)) return 0;
     if (g.M >= (1 << 24) || g.N >= (1 << 24) || g.lda >= (1 << 23) || g.ldb >= (1 << 23)) return 0;   // 24-bit factors of the staging offsets
     if (e.scale != 1.0f) return 0;                                // the bias rides in as the accumulators' initial value
+    if (e.rscale) return 0;                                       // per-row-group gate (stochastic depth): the ring kernels' epilogue
     if ((e.act && e.act != 1 && e.act != 4) || (e.dact && (e.dact != 1 || e.bias))) return 0;   // epilogues are built for GELU / GELU' (a data gradient: no bias) only
     if (e.res2 && (!e.res1 || e.dact || e.act)) return 0;             // gated two-residual form; e.pre = the saved pre-gate value
     if (e.res1 && !e.res2 && (e.gate || e.dact || e.act || e.pre)) return 0;

@@ -523,10 +523,57 @@ __global__ void dropout_add_mixed_kernel(const TX* __restrict__ x, const bf16_t*
     }
 }
 
+// stochastic depth (timm DropPath, video_transformer.py:206,222,226): one multiplier per sample, floor(keep + u_b) / keep with
+// keep = 1 - p -- u_b from the counter-based hash of the dropout kernels (same function of seed and index, same keep rule u >= p)
+__global__ void drop_path_scales_kernel(float* __restrict__ out, int B, float p, unsigned int seed) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    const unsigned int h = fmix32_e(seed ^ fmix32_e((unsigned int)i * 0x9E3779B1u + 0x7F4A7C15u));
+    const float u = (float)(h >> 8) * (1.0f / 16777216.0f);
+    out[i] = u >= p ? 1.0f / (1.0f - p) : 0.f;
+}
+
+// y[r, :] = m[r / S] * x[r, :] over a row-major [M, D] matrix (D % 4 == 0): the gradient that enters a dropped-path branch
+// (the operand of its weight / bias gradients and of its data gradient); m = 0 gives exact zeros
+template <typename T>
+__global__ void scale_rows_kernel(const T* __restrict__ x, const float* __restrict__ m, T* __restrict__ y, int M, int D, int S) {
+    const long long nv = (long long)M * (D / 4);
+    const int dv = D / 4;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long long)gridDim.x * blockDim.x) {
+        const int row = (int)(i / dv);
+        const float k = m[row / S];
+        float v[4];
+        ld4(x + i * 4, v);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] *= k;
+        st4(y + i * 4, v);
+    }
+}
+
 }  // namespace egv
 using namespace egv;
 
 #define EGV_ST reinterpret_cast<hipStream_t>(stream)
+
+extern "C" int egv_drop_path_scales(int B, float p, unsigned int seed, float* out, void* stream) {
+    EGV_CHECK(B > 0 && out && p >= 0.f && p < 1.f, "egv_drop_path_scales: B=%d p=%g (B > 0, 0 <= p < 1, out set)", B, (double)p);
+    hipLaunchKernelGGL(drop_path_scales_kernel, dim3((B + 255) / 256), dim3(256), 0, EGV_ST, out, B, p, seed);
+    EGV_LAUNCH_CHECK();
+    return 0;
+}
+
+// internal (egv_block.cpp): y = m[row / S] * x, x / y [M, D] of dtype
+int egv_scale_rows(int dtype, const void* x, const float* m, void* y, int M, int D, int S, void* stream) {
+    EGV_CHECK(M > 0 && D % 4 == 0 && S > 0 && M % S == 0 && m, "egv_scale_rows: M=%d D=%d S=%d", M, D, S);
+    long long nb = ((long long)M * (D / 4) + 255) / 256;
+    if (nb > 4096) nb = 4096;
+    if (dtype == EGV_BF16)
+        hipLaunchKernelGGL(scale_rows_kernel<bf16_t>, dim3((int)nb), dim3(256), 0, EGV_ST, (const bf16_t*)x, m, (bf16_t*)y, M, D, S);
+    else
+        hipLaunchKernelGGL(scale_rows_kernel<float>, dim3((int)nb), dim3(256), 0, EGV_ST, (const float*)x, m, (float*)y, M, D, S);
+    EGV_LAUNCH_CHECK();
+    return 0;
+}
 
 extern "C" int egv_im2col(int dtype, const float* video, void* out, int BF, int C, int H, int W, int P, void* stream) {
     EGV_CHECK(W % 4 == 0 && H % P == 0 && W % P == 0, "egv_im2col: unsupported geometry H=%d W=%d P=%d", H, W, P);

@@ -97,13 +97,16 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T* __restrict_
 #ifndef EGV_SUMLN_ROWS
 #define EGV_SUMLN_ROWS 1
 #endif
-template <int R>                                                   // rows per wave, all of their loads in flight together
+// DP (stochastic depth, video_transformer.py:222,226): d1 / d2 enter the sum scaled by the multiplier of the row's sample,
+// m1[row / S] / m2[row / S] (either may be NULL = 1); DP = false is the kernel without them.
+template <int R, bool DP>                                          // rows per wave, all of their loads in flight together
 __global__ __launch_bounds__(256) void sum_ln_kernel(const float* __restrict__ base32, const bf16_t* __restrict__ base16,
                                                      const bf16_t* d1, const bf16_t* d2, const bf16_t* dg,      // (sum16 may alias one of them)
                                                      const float* __restrict__ gate,
                                                      float* __restrict__ sum32, bf16_t* sum16, bf16_t* __restrict__ y,
                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                     float* __restrict__ stats, int M, int D, float eps) {
+                                                     float* __restrict__ stats, int M, int D, float eps,
+                                                     const float* __restrict__ m1, const float* __restrict__ m2, int S) {
     const int lane = threadIdx.x & 63;
     const int row0 = (blockIdx.x * 4 + wave_id()) * R;
     if (row0 >= M) return;
@@ -131,6 +134,12 @@ __global__ __launch_bounds__(256) void sum_ln_kernel(const float* __restrict__ b
         const bool live = row0 + r < M;
         const size_t ro = (size_t)min(row0 + r, M - 1) * D;
         s[r] = 0.f;
+        float k1 = 1.f, k2 = 1.f;
+        if constexpr (DP) {
+            const int smp = min(row0 + r, M - 1) / S;
+            if (m1) k1 = m1[smp];
+            if (m2) k2 = m2[smp];
+        }
 #pragma unroll
         for (int j = 0; j < LN_MAXV; ++j) {
             const int c = (j * 64 + lane) * 4;
@@ -138,8 +147,13 @@ __global__ __launch_bounds__(256) void sum_ln_kernel(const float* __restrict__ b
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float a = v[r][j][e];
-                    if (d1) a += t1[r][j][e];
-                    if (d2) a += t2[r][j][e];
+                    if constexpr (DP) {
+                        if (d1) a += k1 * t1[r][j][e];
+                        if (d2) a += k2 * t2[r][j][e];
+                    } else {
+                        if (d1) a += t1[r][j][e];
+                        if (d2) a += t2[r][j][e];
+                    }
                     if (dg) a += gt * t3[r][j][e];
                     v[r][j][e] = a;
                 }
@@ -703,9 +717,11 @@ extern "C" int egv_layernorm_fwd_res32(const float* x, float* y, void* y16, cons
     return 0;
 }
 
-extern "C" int egv_sum_layernorm(const float* base32, const void* base16, const void* d1, const void* d2, const void* dg, const float* gate,
-                                 float* sum32, void* sum16, void* y, const float* gamma, const float* beta, float* stats, int M, int D,
-                                 float eps, void* stream) {
+// egv_sum_layernorm with per-sample multipliers of the two Linear-output terms (stochastic depth of the block executor, egv_block.cpp):
+// s = base + m1[row / S] * d1 + m2[row / S] * d2 + gate * dg; m1 == m2 == NULL is egv_sum_layernorm, launch and bits
+int egv_sum_layernorm_dp(const float* base32, const void* base16, const void* d1, const void* d2, const void* dg, const float* gate,
+                         float* sum32, void* sum16, void* y, const float* gamma, const float* beta, float* stats, int M, int D,
+                         float eps, const float* m1, const float* m2, int S, void* stream) {
     EGV_CHECK(D % 4 == 0 && D <= LN_MAXV * 256 && M > 0, "egv_sum_layernorm: M=%d D=%d unsupported", M, D);
     EGV_CHECK((base32 != nullptr) != (base16 != nullptr), "egv_sum_layernorm: exactly one of base32 / base16");
     EGV_CHECK(!y || (gamma && beta), "egv_sum_layernorm: LayerNorm output without its affine terms");
@@ -713,10 +729,24 @@ extern "C" int egv_sum_layernorm(const float* base32, const void* base16, const 
     double bytes = (double)M * D * ((base32 ? 4 : 2) + (d1 ? 2 : 0) + (d2 ? 2 : 0) + (dg ? 2 : 0) + (sum32 ? 4 : 0) + (sum16 ? 2 : 0) + (y ? 2 : 0));
     LnProf prof(stream, 30, bytes);
     constexpr int R = EGV_SUMLN_ROWS;
-    hipLaunchKernelGGL(sum_ln_kernel<R>, dim3((M + 4 * R - 1) / (4 * R)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), base32, (const bf16_t*)base16,
-                       (const bf16_t*)d1, (const bf16_t*)d2, (const bf16_t*)dg, gate, sum32, (bf16_t*)sum16, (bf16_t*)y, gamma, beta, stats, M, D, eps);
+    if (m1 || m2) {
+        EGV_CHECK(S > 0 && M % S == 0, "egv_sum_layernorm: %d rows are not whole samples of %d", M, S);
+        hipLaunchKernelGGL((sum_ln_kernel<R, true>), dim3((M + 4 * R - 1) / (4 * R)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), base32,
+                           (const bf16_t*)base16, (const bf16_t*)d1, (const bf16_t*)d2, (const bf16_t*)dg, gate, sum32, (bf16_t*)sum16, (bf16_t*)y,
+                           gamma, beta, stats, M, D, eps, m1, m2, S);
+    } else {
+        hipLaunchKernelGGL((sum_ln_kernel<R, false>), dim3((M + 4 * R - 1) / (4 * R)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), base32,
+                           (const bf16_t*)base16, (const bf16_t*)d1, (const bf16_t*)d2, (const bf16_t*)dg, gate, sum32, (bf16_t*)sum16, (bf16_t*)y,
+                           gamma, beta, stats, M, D, eps, nullptr, nullptr, 1);
+    }
     EGV_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int egv_sum_layernorm(const float* base32, const void* base16, const void* d1, const void* d2, const void* dg, const float* gate,
+                                 float* sum32, void* sum16, void* y, const float* gamma, const float* beta, float* stats, int M, int D,
+                                 float eps, void* stream) {
+    return egv_sum_layernorm_dp(base32, base16, d1, d2, dg, gate, sum32, sum16, y, gamma, beta, stats, M, D, eps, nullptr, nullptr, 1, stream);
 }
 
 static inline int ln_bwd_blocks(int M) {

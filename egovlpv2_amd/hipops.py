@@ -1269,7 +1269,7 @@ class VideoBlockFn(Function):
     ORDER_FUSED = list(range(18)) + [20, 21, 22, 23, 18, 19, 24, 25, 26]
 
     @staticmethod
-    def _desc(cfg, x, y, y_mask, params):
+    def _desc(cfg, x, y, y_mask, params, dp=None):
         B, Fr, N, H, Hd, eps, L_, _track, fp8 = cfg[:9]
         fused = L_ > 0
         d = L.VBlockDesc()
@@ -1294,6 +1294,8 @@ class VideoBlockFn(Function):
             d.ln_g[3], d.ln_b[3] = _p(params[24]), _p(params[25])
             d.alpha = _p(params[26])
             d.y, d.y_mask = _p(y), _p(y_mask)
+        if dp is not None:                               # stochastic depth: per-sample multipliers of the space / MLP branch
+            d.dp_scale[0], d.dp_scale[1] = _p(dp[0]), _p(dp[1])
         d.stream = _st()
         d.fwd_cus = _fwd_cus[0]
         return d
@@ -1302,7 +1304,8 @@ class VideoBlockFn(Function):
     def forward(ctx, cfg, x, y, y_mask, *params):
         _need_gpu(x)
         assert x.dim() == 2 and x.is_contiguous()
-        d = VideoBlockFn._desc(cfg, x, y, y_mask, params)
+        dp = cfg[15] if len(cfg) > 15 else None
+        d = VideoBlockFn._desc(cfg, x, y, y_mask, params, dp)
         out = torch.empty_like(x)
         res32, x32 = cfg[9], cfg[10]
         out32 = None
@@ -1338,6 +1341,7 @@ class VideoBlockFn(Function):
         d.out, d.save, d.save_bytes, d.ws, d.ws_bytes = _p(out), _p(save), nsave, _p(ws), ws.numel()
         check(lib.egv_vblock_fwd(C.byref(d)), 'egv_vblock_fwd')
         ctx.cfg = cfg[:9]
+        ctx.dp = dp                                      # (the backward call, and a recomputed forward, use the same multipliers)
         ctx.key = ('v', id(params[0]))
         ctx.tail = bool(cfg[7] and _first_vblock[0] and SW.on('EGV_WGRAD_TAIL'))
         if cfg[7]:
@@ -1368,7 +1372,7 @@ class VideoBlockFn(Function):
         dout = dout.contiguous()
         if ctx.recompute is not None:
             res32, x32 = ctx.recompute
-            df = VideoBlockFn._desc(cfg, x, y, y_mask, params)
+            df = VideoBlockFn._desc(cfg, x, y, y_mask, params, ctx.dp)
             out_r = torch.empty_like(x)
             out32_r = None
             if res32:
@@ -1381,7 +1385,7 @@ class VideoBlockFn(Function):
             df.out, df.save, df.save_bytes, df.ws, df.ws_bytes = _p(out_r), _p(save), nsave, _p(wsf), wsf.numel()
             check(lib.egv_vblock_fwd(C.byref(df)), 'egv_vblock_fwd(recompute)')
             del out_r, out32_r
-        d = VideoBlockFn._desc(cfg, x, y, y_mask, params)
+        d = VideoBlockFn._desc(cfg, x, y, y_mask, params, ctx.dp)
         dx = torch.empty_like(x)
         dy = torch.empty_like(y) if (fused and ctx.needs_input_grad[2]) else None
         d.stream2 = _side_stream_ptr()
@@ -1608,7 +1612,16 @@ def stream32(x):
     return getattr(x, '_res32', None)
 
 
-def video_block(x, params, B, Fr, N, H, Hd, eps, y=None, y_mask=None, L=0, fp8=False, next_ln=None, recompute=False):
+def drop_path_scales(B, p, seed, device=None):
+    """per-sample stochastic-depth multipliers floor(keep + u_b) / keep, keep = 1 - p (timm DropPath, video_transformer.py:206): a
+    [B] fp32 tensor drawn on the device from `seed` (egv_drop_path_scales -- no host synchronisation, no torch generator)"""
+    out = torch.empty(int(B), dtype=torch.float32, device='cuda' if device is None else device)
+    _need_gpu(out)
+    check(lib.egv_drop_path_scales(int(B), float(p), int(seed) & 0xFFFFFFFF, _p(out), _st()), 'egv_drop_path_scales')
+    return out
+
+
+def video_block(x, params, B, Fr, N, H, Hd, eps, y=None, y_mask=None, L=0, fp8=False, next_ln=None, recompute=False, dp_scale=None):
     """fp8: the forward / dgrad GEMMs over the video tokens on MX-fp8 operands (bf16 mode only; BASELINE.json configs[4]).
     With EGV_VIDEO_RES32 (bf16 mode) the residual stream is fp32, as under the reference's autocast (trainer_egoclip.py:143): the
     returned bf16 tensor -- the one autograd sees, GEMMs read and the backward pass uses -- carries its fp32 value as `._res32`,
@@ -1619,7 +1632,14 @@ def video_block(x, params, B, Fr, N, H, Hd, eps, y=None, y_mask=None, L=0, fp8=F
     recompute: activation checkpointing (the reference's yml `use_checkpoint`, model.py:239-266,326: torch.utils.checkpoint around every
     block) -- the call keeps its inputs only; its backward call first re-runs the forward into a fresh save buffer (bitwise the first
     run: same kernels, same inputs, no dropout in a video block), then runs the backward.  0.85 GB less per block call at configs[2],
-    one more forward per block."""
+    one more forward per block.
+    dp_scale = (m_attn, m_mlp): stochastic depth (video_transformer.py:222,226) -- [B] fp32 device tensors (drop_path_scales) that scale
+    the space branch and the MLP branch per sample, in forward and backward (and in a recomputed forward); None: no drop path.
+    The executor refuses them for a fused block (y given) and with fp8."""
+    if dp_scale is not None:
+        dp_scale = tuple(m.to(device=x.device, dtype=torch.float32).contiguous() for m in dp_scale)
+        if len(dp_scale) != 2 or any(m.shape != (B,) for m in dp_scale):
+            raise ValueError('video_block: dp_scale must be two [B] tensors (space branch, MLP branch)')
     res32 = video_res32(x, fp8)
     recompute = bool(recompute) and _tracks_grad(params) and not fp8
     pre = None
@@ -1633,7 +1653,7 @@ def video_block(x, params, B, Fr, N, H, Hd, eps, y=None, y_mask=None, L=0, fp8=F
         if next_ln is not None and not SW.on('EGV_LN_FOLD'):
             next_ln = None
     cfg = (B, Fr, N, H, Hd, float(eps), L if y is not None else 0, _tracks_grad(params), bool(fp8), res32, stream32(x) if res32 else None,
-           pre, next_ln if res32 else None, ((not torch.is_grad_enabled()) and SW.on('EGV_INFER_LEAN')) or recompute, recompute)
+           pre, next_ln if res32 else None, ((not torch.is_grad_enabled()) and SW.on('EGV_INFER_LEAN')) or recompute, recompute, dp_scale)
     if not res32:
         return VideoBlockFn.apply(cfg, x, y, y_mask, *params)
     out, out32, nsv = VideoBlockFn.apply(cfg, x, y, y_mask, *params)

@@ -434,7 +434,25 @@ class FrozenInTime(nn.Module):
             next_ln = (pn[12], pn[13], next_block[1], bool(len(next_block) > 2 and next_block[2]))
         return ops.video_block(x, self._block_params('video', i, y is not None), B, c.frames, c.n_patches, c.heads, c.dim * c.mlp_ratio,
                                c.eps_video, y=y, y_mask=y_mask, L=L, fp8=bool(self.__dict__.get('_mx_weights')), next_ln=next_ln,
-                               recompute=self.act_checkpoint)
+                               recompute=self.act_checkpoint, dp_scale=self._drop_path_scales(i, B, x.device))
+
+    def _drop_path_scales(self, i, B, device):
+        """stochastic depth of video block i (video_transformer.py:206,222,226): (m_attn, m_mlp), the per-sample multipliers of its
+        space and MLP branches, or None.  Only a model with drop-path rates (`_dp_rates`: the fine-tune variant) in train mode
+        (module.training, as timm's DropPath) draws, and only for a block with a rate > 0 -- two seeds of the model's own dropout
+        stream (_drop_seed), so at rate 0 that stream is what it is without drop path.  Each call is recorded in
+        last_drop_path_scales[i] (all ones for a block with rate 0)."""
+        rates = getattr(self, '_dp_rates', None)
+        if not rates or not self.training:
+            return None
+        p = rates[i]
+        if p <= 0.0:
+            ones = torch.ones(B, dtype=torch.float32, device=device)
+            self.last_drop_path_scales[i] = (ones, ones)
+            return None
+        m = (ops.drop_path_scales(B, p, self._drop_seed(), device), ops.drop_path_scales(B, p, self._drop_seed(), device))
+        self.last_drop_path_scales[i] = m
+        return m
 
     def _tail_ok(self, x):
         """may the LAST block of a video pass run in its CLS-only form (_video_block_tail)?  bf16 storage with the fp32 residual stream,
@@ -467,9 +485,12 @@ class FrozenInTime(nn.Module):
         pfx = f'video_model.blocks.{i}'
         D = c.dim
         qkv, xc = head
+        dp = self._drop_path_scales(i, B, qkv.device)                                     # stochastic depth of the two branches (:222, :226)
+        if dp is not None and fused:
+            raise ValueError('drop path is not supported in the fused video blocks')
         ctx = ops.cls_attention(qkv, B, c.seq, c.heads)                                   # the CLS query over all S keys (:129)
         s = self._lin(ctx, pfx + '.attn.proj')                                            # (B, D)
-        sr = xc + s.float()                                                               # residual from x, not from the time residual (:222)
+        sr = xc + (s.float() if dp is None else dp[0][:, None] * s.float())              # residual from x, not from the time residual (:222)
         if fused:
             a = pfx + '.attn'                                                             # image-to-text cross attention (:155-185)
             kv = self._lin(y, a + '.qkv_text_i2t')
@@ -477,7 +498,8 @@ class FrozenInTime(nn.Module):
             o = ops.plain_attention(q, kv[:, :D], kv[:, D:], B, c.heads, 1, L, 0.125, mask=y_mask)
             sr = sr + self.p(a + '.alpha_i2t') * self._lin(o, a + '.proj_i2t').float()
         h2 = ops.CastFn.apply(self._ln(sr, pfx + '.norm2', c.eps_video), self.compute_dtype)
-        out = sr + self._lin(self._lin(h2, pfx + '.mlp.fc1', act='gelu'), pfx + '.mlp.fc2').float()
+        mlp = self._lin(self._lin(h2, pfx + '.mlp.fc1', act='gelu'), pfx + '.mlp.fc2').float()
+        out = sr + (mlp if dp is None else dp[1][:, None] * mlp)
         out._cls_rows32 = True
         return out
 
@@ -604,6 +626,8 @@ class FrozenInTime(nn.Module):
         reaches the tower (1.0 -> 0.45 ms of calling-stream idle time in front of the tower's backward)."""
         self._prepare_weights()          # (a no-op when the step's copies exist: direct compute_video / Feature_Extraction calls find them too)
         B = video_data.shape[0]
+        if getattr(self, '_dp_rates', None):
+            self.last_drop_path_scales = {}                              # block index -> (m_attn, m_mlp) of this pass (_drop_path_scales)
         x = self._patch_tokens(video_data, 'video_model.cls_token')
         last = self.cfg.depth - 1
         for i in range(last):

@@ -2,8 +2,14 @@
 HIP block executor, 256-d projection heads (txt ReLU-Linear, vid Linear; :116-119) and the `Dual` task -- both towers, cosine
 similarity of the gathered embeddings, a ranking loss (:410-444).  EPIC-Kitchens MIR pairs it with
 AdaptiveMaxMarginRankingLoss weighted by the batch's `relation` field (configs/ft/epic.json:57-62), Charades-Ego with
-NormSoftmaxLoss (configs/ft/charades.json:57-61); both are in model/loss.py here.  drop_path_rate must be 0 (it is in both
-reference configs): the block executor has no stochastic depth."""
+NormSoftmaxLoss (configs/ft/charades.json:57-61); both are in model/loss.py here.
+
+video_params['drop_path_rate'] (:83) is stochastic depth as in the reference's SpaceTimeTransformer: block i has the rate
+linspace(0, drop_path_rate, depth)[i] (video_transformer.py:297), and in train mode each call of a block with a rate > 0 scales its
+space-attention branch and its MLP branch by per-sample multipliers floor(keep + u) / keep (timm DropPath, :206,222,226; the time
+branch is never scaled).  The multipliers are drawn on the device from the model's dropout seed stream (seed_dropout restarts it),
+applied inside the block executor's kernels (hipops.video_block(dp_scale=...)), and those of the last forward are kept in
+`last_drop_path_scales` (block index -> (m_attn, m_mlp)).  Eval mode, or a rate of 0, is the block without drop path."""
 from __future__ import annotations
 
 import torch
@@ -19,8 +25,9 @@ class FrozenInTime(_PretrainModel):
                  compute_dtype=torch.bfloat16, path_config: PathConfig | None = None, init_seed: int = 0):
         """Same signature as the reference constructor (:45-56).  projection='minimal' means 256-d heads whatever
         projection_dim says (:116-119)."""
-        if float(video_params.get('drop_path_rate', 0.0)) != 0.0:
-            raise NotImplementedError("drop_path_rate != 0: stochastic depth is not implemented in the block executor")
+        drop_path_rate = float(video_params.get('drop_path_rate', 0.0))
+        if not 0.0 <= drop_path_rate < 1.0:
+            raise ValueError(f"drop_path_rate must be in [0, 1), got {drop_path_rate}")
         yml = dict(DEFAULT_YML, **(config or {}))
         if path_config is None:
             path_config = PathConfig(depth=yml['num_layers'], n_fuse=yml['num_fuse_block'], frames=video_params['num_frames'],
@@ -33,6 +40,10 @@ class FrozenInTime(_PretrainModel):
                          projection=projection, load_temporal_fix=load_temporal_fix, config=config, task_names=task_names,
                          norm_layer=norm_layer, embed_dim=embed_dim, compute_dtype=compute_dtype, path_config=path_config,
                          init_seed=init_seed)
+        self.drop_path_rate = drop_path_rate
+        # per-block rates (video_transformer.py:297); None: no block ever drops (no seed of the dropout stream is spent on it)
+        self._dp_rates = [r.item() for r in torch.linspace(0, drop_path_rate, path_config.depth)] if drop_path_rate > 0 else None
+        self.last_drop_path_scales = {}
 
     def forward(self, data, allgather, n_gpu, args, config, loss_dual, gpu, return_embeds=True, task_names='Dual',
                 dataset_name='charades'):

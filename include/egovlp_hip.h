@@ -361,6 +361,14 @@ typedef struct egv_vblock_desc {
     /* egv_vblock_bwd: bit w set = the weight / bias gradient of Linear slot w is ADDED to dw[w] / db[w] (egv_wgrad_problem::accumulate) -- honoured by
      * the grouped weight-gradient launch only (egv_vblock_bwd_groups(d) == 1); a caller must not set bits otherwise. */
     unsigned int acc_mask;
+    /* Stochastic depth (timm DropPath of SpaceTimeBlock, video_transformer.py:206,222,226; rates from drop_path_rate, :297): per-sample
+     * multipliers, device arrays of B fp32 values (egv_drop_path_scales), dp_scale[0] for the space branch, dp_scale[1] for the MLP
+     * branch; NULL = no drop path on that branch.  sr = x + dp_scale[0][b] * proj(space attention) (the base is x, :222), out = sr +
+     * dp_scale[1][b] * fc2(..) (:226), b = row / S; the time branch is never scaled (:218).  Forward: the residual epilogue of
+     * attn.proj / mlp.fc2, or with EGV_BLOCK_RES_F32 the sums of egv_sum_layernorm.  Backward (same pointers, same values): the
+     * gradients entering the two branches are the scaled ones -- exactly zero for a dropped sample.  Refused (error) with L > 0,
+     * EGV_BLOCK_FP8 and EGV_BLOCK_HEAD.  Both NULL: every launch and every bit as without the fields. */
+    const float* dp_scale[2];
 } egv_vblock_desc;
 #define EGV_BLOCK_HEAD 32     /* egv_vblock_fwd / _bwd (EGV_BLOCK_RES_F32 form): only the part of the block every output row depends on -- norm3, the
                                  time attention with its projection and residual, norm1 and the space attention's qkv projection
@@ -374,6 +382,10 @@ typedef struct egv_vblock_desc {
                                  store; not with EGV_BLOCK_FP8) and, with EGV_BLOCK_RES_F32, the bf16 roundings of the two inner residual sums.
                                  Outputs are bitwise those of a call without the flag. */
 #define EGV_BLOCK_H3_READY 16 /* egv_vblock_fwd with EGV_BLOCK_RES_F32: the h3 / stats3 slots of `save` were filled by the previous call (next_h / next_stats) */
+/* out[b] = floor(keep + u_b) / keep, keep = 1 - p, b < B (0 <= p < 1): the per-sample multipliers of stochastic depth (timm
+ * DropPath, video_transformer.py:206 -- x.div(keep) * floor(keep + rand)), u_b a counter-based function of (seed, b) -- the hash
+ * and keep rule of egv_dropout_add -- so the draw is stream-ordered, needs no host synchronisation and no torch generator. */
+int egv_drop_path_scales(int B, float p, unsigned int seed, float* out, void* stream);
 long long egv_vblock_save_bytes(const egv_vblock_desc* d);
 /* byte offsets of the stats3 [M][2] fp32 and h3 [M, D] slots inside a save buffer of this geometry */
 int egv_vblock_next_slots(const egv_vblock_desc* d, long long* stats3_off, long long* h3_off);
