@@ -14,6 +14,7 @@ struct GemmEpi {
     int act;             // 0 none, 1 gelu(erf), 2 relu, 3 tanh
     int dact;            // 0 none, 1 gelu'(aux = pre-activation), 2 relu'(aux = output), 3 tanh'(aux = output)
     int ldr;             // leading dim of res1/res2/pre/aux
+    int r_vec_ok;        // res1/res2/pre/aux all aligned to a 4-element vector (host-checked): the epilogue may move them 4 at a time
     float scale;         // host scalar applied to the accumulator first
     unsigned char* oq = nullptr;   // MX-fp8 form only: the output also as e4m3 codes [M][N] ...
     unsigned char* os = nullptr;   // ... and role-0 scale bytes (egv_mx.hip)
@@ -66,7 +67,7 @@ __device__ __forceinline__ void gemm_epilogue4(const GemmArgs& g, OutT* C, int m
     const T* R2 = reinterpret_cast<const T*>(e.res2);
     const T* AUX = reinterpret_cast<const T*>(e.aux);
     T* PRE = reinterpret_cast<T*>(e.pre);
-    const bool rvec = (e.ldr & 3) == 0;
+    const bool rvec = e.r_vec_ok && (e.ldr & 3) == 0;
     const bool full = (n + 3 < g.N);
     const size_t ro = (size_t)m * e.ldr + n;
 #pragma unroll

@@ -372,6 +372,11 @@ extern "C" int egv_gemm(int dtype, int a_trans, int b_trans, int M, int N, int K
     g.tiles_n = (N + BN - 1) / BN;
     g.e.bias = bias; g.e.gate = gate; g.e.res1 = res1; g.e.res2 = res2; g.e.pre = pre; g.e.aux = aux;
     g.e.act = act; g.e.dact = dact; g.e.ldr = ldr ? ldr : ldc; g.e.scale = scale;
+    {   // 4-element epilogue vectors: 8 bytes (bf16) / 16 bytes (fp32) per access of res1 / res2 / pre / aux
+        const uintptr_t am = dtype == EGV_BF16 ? 7 : 15;
+        auto al = [am](const void* p) { return (reinterpret_cast<uintptr_t>(p) & am) == 0; };
+        g.e.r_vec_ok = al(res1) && al(res2) && al(pre) && al(aux);
+    }
     g.e.rscale = t_row_scale; g.e.rgroup = t_row_group;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const double es_ = dtype == EGV_BF16 ? 2.0 : 4.0;

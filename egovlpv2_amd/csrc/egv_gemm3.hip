@@ -853,7 +853,7 @@ int egv_gemm3_launch(const GemmArgs& gin, hipStream_t st) {
     const GemmEpi& e = g.e;
     if ((g.K % 64) || g.K < 192 || (g.N % 64) || !g.a_vec_ok || !g.b_vec_ok) return 0;
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    if ((g.ldc % 8) || (e.ldr % 8) || !al16(g.C) || !al16(e.res1) || !al16(e.pre) || !al16(e.aux) || (e.bias && !al16(e.bias))) return 0;
+    if ((g.ldc % 8) || (e.ldr % 8) || !al16(g.C) || !al16(e.res1) || !al16(e.res2) || !al16(e.pre) || !al16(e.aux) || (e.bias && !al16(e.bias))) return 0;
     if ((long long)g.M * g.lda >= (1LL << 30) || (long long)g.N * g.ldb >= (1LL << 30)) return 0;   // 32-bit byte offsets
     if ((long long)g.M * g.ldc >= (1LL << 30) || (long long)g.M * e.ldr >= (1LL << 30)) return 0;
     if (g.M >= (1 << 24) || g.N >= (1 << 24) || g.lda >= (1 << 23) || g.ldb >= (1 << 23)) return 0;   // 24-bit factors of the staging offsets
