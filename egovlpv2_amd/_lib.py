@@ -149,6 +149,7 @@ PROTOTYPES = {
     'egv_attn_fewq_workspace_bytes': (i64, [i32, i32, i32, i32]),
     'egv_attn_bwd_pair_covers_extra': (i32, [i32, C.POINTER(AttnDesc)]),
     'egv_attn_bwd_extra_reduce': (i32, [i32, C.POINTER(AttnDesc), i32, vp]),
+    'egv_attn_last_path': (i32, []),
     'egv_im2col': (i32, [i32, vp, vp, i32, i32, i32, i32, i32, vp]),
     'egv_im2col_u8': (i32, [i32, vp, vp, i32, i32, i32, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), vp]),
     'egv_assemble_tokens': (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),

@@ -85,6 +85,11 @@ static inline egv::AttnArgs to_args(const egv_attn_desc* d) {
 }
 
 
+// Path record of the last attention entry call on this thread (egv_attn_last_path, egv_attn.hip): the dispatchers note the kind of
+// path they enqueued, the sub-launchers the tile instance they chose (kind * 100 + variant; 0 = nothing enqueued).
+void egv_attn_note_path(int kind);
+void egv_attn_note_variant(int variant);
+
 // MFMA launchers (egv_attn_mfma.hip): return 1 if the problem shape is covered (and the kernel was enqueued), else 0.
 int egv_attn_fwd_mfma(const egv::AttnArgs& a, int B, hipStream_t st);     // 2: the extra row's partial states were written too
 bool egv_attn_fwd_cls_ok(const egv::AttnArgs& a);

@@ -130,7 +130,9 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnArgs a) {
         const long long row = rs_row(a.q, b, g, q0 + i);
         const float m = sM[(w * QPW + i) * 2], l = sM[(w * QPW + i) * 2 + 1];
         if (a.nsplit == 1) {
-            Elem<T>::st(O + row * a.ldo + ho + lane, sO[(w * QPW + i) * HD + lane] / l);
+            const float o = sO[(w * QPW + i) * HD + lane] / l;
+            Elem<T>::st(O + row * a.ldo + ho + lane, o);
+            if (a.O32) a.O32[row * a.ldo + ho + lane] = o;
             if (a.lse && lane == 0) a.lse[row * a.H + h] = m + __logf(l);
         } else {
             // partial (m, l, o[64]) per split: ws[split][P * q.n own rows][H][66]
@@ -198,7 +200,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(const AttnArgs a) 
     for (int i = 0; i < nq; ++i) {
         const long long row = rs_row(a.q, b, g, q0 + i);
         const float dov = Elem<T>::ld(dO + row * a.ldo + ho + lane);
-        const float ov = Elem<T>::ld(O + row * a.ldo + ho + lane);
+        const float ov = a.O32 ? a.O32[row * a.ldo + ho + lane] : Elem<T>::ld(O + row * a.ldo + ho + lane);   // egv_attn_desc::O32
         sQ[(w * QPW + i) * HD + lane] = Elem<T>::ld(Q + row * a.ldq + hq + lane) * a.scale;
         sDO[(w * QPW + i) * HD + lane] = dov;
         sDQ[(w * QPW + i) * HD + lane] = 0.f;
@@ -641,6 +643,12 @@ static inline size_t dkv_smem() { return (size_t)(2 * TK * LDT) * 4; }
 }  // namespace egv
 using namespace egv;
 
+static thread_local int t_attn_kind = 0, t_attn_variant = 0;
+void egv_attn_note_path(int kind) { t_attn_kind = kind; }
+void egv_attn_note_variant(int variant) { t_attn_variant = variant; }
+static void reset_path() { t_attn_kind = 0; t_attn_variant = 0; }
+extern "C" int egv_attn_last_path(void) { return t_attn_kind * 100 + t_attn_variant; }
+
 static int check_desc(const egv_attn_desc* d, const char* who) {
     EGV_CHECK(d->B > 0 && d->G > 0 && d->H > 0 && d->q_n > 0 && d->k_n > 0, "%s: bad problem shape", who);
     EGV_CHECK(!(d->drop_p > 0.f) || (d->extra == 0 && d->drop_p < 1.f && d->q_n > 1 && d->k_n > 1),
@@ -693,17 +701,21 @@ static int egv_attn_fwd_impl(int dtype, const egv_attn_desc* d, void* stream) {
     AttnArgs a = to_args(d);
     if (dtype == EGV_BF16 && a.nsplit == 1) {
         if (egv_attn_fewkeys_fwd(a, d->B, st)) {    // many queries over <= 32 keys (image -> text cross attention): egv_attn_cross.hip
+            egv_attn_note_path(1);
             EGV_LAUNCH_CHECK();
             return 0;
         }
         if (d->ws && d->ws_bytes >= egv_attn_fwd_extra_workspace_bytes(d->B, d->G, d->H) && egv_attn_time_fwd(a, d->B, st)) {
+            egv_attn_note_path(2);
             EGV_LAUNCH_CHECK();                  // <= 16-row groups (time attention): group rows and the CLS query in one launch + its combination
             return 0;
         }
         {   // long groups (space attention): row-major LDS images, the CLS row as row n of them (egv_attn_space.hip)
             AttnArgs a2 = a;
             if (!(d->ws && d->ws_bytes >= egv_attn_fwd_extra_workspace_bytes(d->B, d->G, d->H))) a2.ws = nullptr;
-            if (egv_attn_space_fwd(a2, d->B, st)) {
+            const int rs = egv_attn_space_fwd(a2, d->B, st);
+            if (rs) {
+                egv_attn_note_path(rs == 2 ? 4 : 3);
                 EGV_LAUNCH_CHECK();
                 return 0;
             }
@@ -712,6 +724,7 @@ static int egv_attn_fwd_impl(int dtype, const egv_attn_desc* d, void* stream) {
             EGV_CHECK(d->ws_bytes >= egv_attn_fwd_extra_workspace_bytes(d->B, d->G, d->H), "egv_attn_fwd: workspace too small for the extra row's partial states");
         const int r = egv_attn_fwd_mfma(a, d->B, st);
         if (r) {
+            egv_attn_note_path(r == 2 ? 6 : 5);
             EGV_LAUNCH_CHECK();
             if (r == 2) {                        // the extra row as a query: combine its G partial states (one per group)
                 AttnArgs c = a;
@@ -727,6 +740,7 @@ static int egv_attn_fwd_impl(int dtype, const egv_attn_desc* d, void* stream) {
     }
     if (dtype == EGV_BF16 && d->ws && d->q_n <= 32 && d->ws_bytes >= egv_attn_fewq_workspace_bytes(d->B, d->G, d->H, d->k_n) &&
         egv_attn_fewq_fwd(a, d->B, st)) {              // <= 32 queries over many keys (text -> image cross attention): egv_attn_cross.hip
+        egv_attn_note_path(7);
         EGV_LAUNCH_CHECK();
         return 0;
     }
@@ -734,12 +748,14 @@ static int egv_attn_fwd_impl(int dtype, const egv_attn_desc* d, void* stream) {
         EGV_CHECK(d->ws && d->ws_bytes >= egv_attn_split_workspace_bytes(0, d->B, d->G, d->H, d->q_n, a.nsplit),
                   "egv_attn_fwd: workspace too small");
     if (d->q_n == 1 && a.nsplit > 1) {
+        egv_attn_note_path(8);
         dim3 grid1(a.nsplit, d->B * d->G, d->H);
         if (dtype == EGV_BF16) hipLaunchKernelGGL(attn1_fwd_kernel<bf16_t>, grid1, dim3(256), 0, st, a);
         else hipLaunchKernelGGL(attn1_fwd_kernel<float>, grid1, dim3(256), 0, st, a);
     } else if (dtype == EGV_BF16 && a.nsplit > 1 && egv_attn_fwd_mfma(a, d->B, st)) {
-        // short query side against a long key side (text -> image): MFMA kernel per key chunk, partial softmax states
+        egv_attn_note_path(9);   // short query side against a long key side (text -> image): MFMA kernel per key chunk, partial softmax states
     } else {
+        egv_attn_note_path(a.nsplit > 1 ? 11 : 10);
         const int nw = pick_nw(d->q_n);
         dim3 grid(((d->q_n + nw * QPW - 1) / (nw * QPW)) * a.nsplit, d->B * d->G, d->H);
         const size_t sm = fwd_smem(nw);
@@ -762,6 +778,7 @@ static int egv_attn_bwd_dq_impl(int dtype, const egv_attn_desc* d, void* stream)
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     AttnArgs a = to_args(d);
     if (dtype == EGV_BF16 && a.nsplit == 1 && egv_attn_dq_mfma(a, d->B, st)) {
+        egv_attn_note_path(egv_attn_bwd_pair_cls_ok(a) ? 22 : 21);
         EGV_LAUNCH_CHECK();
         return 0;
     }
@@ -769,11 +786,14 @@ static int egv_attn_bwd_dq_impl(int dtype, const egv_attn_desc* d, void* stream)
         EGV_CHECK(d->ws && d->ws_bytes >= egv_attn_split_workspace_bytes(1, d->B, d->G, d->H, d->q_n, a.nsplit),
                   "egv_attn_bwd_dq: workspace too small");
     if (d->q_n == 1 && a.nsplit > 1) {
+        egv_attn_note_path(24);
         dim3 grid1(a.nsplit, d->B * d->G, d->H);
         if (dtype == EGV_BF16) hipLaunchKernelGGL(attn1_dq_kernel<bf16_t>, grid1, dim3(256), 0, st, a);
         else hipLaunchKernelGGL(attn1_dq_kernel<float>, grid1, dim3(256), 0, st, a);
     } else if (dtype == EGV_BF16 && a.nsplit > 1 && egv_attn_dq_mfma(a, d->B, st)) {
+        egv_attn_note_path(23);
     } else {
+        egv_attn_note_path(a.nsplit > 1 ? 26 : 25);
         const int nw = pick_nw(d->q_n);
         dim3 grid(((d->q_n + nw * QPW - 1) / (nw * QPW)) * a.nsplit, d->B * d->G, d->H);
         const size_t sm = dq_smem(nw);
@@ -801,6 +821,7 @@ static int egv_attn_bwd_dkv_impl(int dtype, const egv_attn_desc* d, void* stream
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     AttnArgs a = to_args(d);
     if (dtype == EGV_BF16 && a.nsplit == 1 && egv_attn_dkv_mfma(a, d->B, st)) {
+        egv_attn_note_path(egv_attn_bwd_pair_cls_ok(a) ? 32 : 31);
         EGV_LAUNCH_CHECK();
         return 0;
     }
@@ -808,12 +829,14 @@ static int egv_attn_bwd_dkv_impl(int dtype, const egv_attn_desc* d, void* stream
         EGV_CHECK(d->ws && d->ws_bytes >= egv_attn_bwd_dkv_workspace_bytes(d->B, d->G, d->H, d->k_n, a.nsplit),
                   "egv_attn_bwd_dkv: workspace too small");
     if (d->k_n == 1 && a.nsplit > 1) {
+        egv_attn_note_path(34);
         dim3 grid1(a.nsplit, d->B * d->G, d->H);
         if (dtype == EGV_BF16) hipLaunchKernelGGL(attn1_dkv_kernel<bf16_t>, grid1, dim3(256), 0, st, a);
         else hipLaunchKernelGGL(attn1_dkv_kernel<float>, grid1, dim3(256), 0, st, a);
     } else if (dtype == EGV_BF16 && a.nsplit > 1 && egv_attn_dkv_mfma(a, d->B, st)) {
-        // long query side, short key side (image->text cross attention): MFMA kernel per query chunk, fp32 partials
+        egv_attn_note_path(33);  // long query side, short key side (image->text cross attention): MFMA kernel per query chunk, fp32 partials
     } else {
+        egv_attn_note_path(a.nsplit > 1 ? 36 : 35);
         const int ntot = d->q_n + d->extra;
         const int per = (ntot + a.nsplit - 1) / a.nsplit;
         const int nw = per >= 4 ? 4 : (per >= 2 ? 2 : 1);
@@ -849,10 +872,12 @@ static int egv_attn_bwd_fused_impl(int dtype, const egv_attn_desc* d, void* stre
     if (d->ws && d->extra)
         EGV_CHECK(d->ws_bytes >= egv_attn_bwd_fused_workspace_bytes(d->B, d->G, d->H), "egv_attn_bwd_fused: workspace too small");
     if (!d->extra && d->ws && d->ws_bytes >= egv_attn_fewkeys_workspace_bytes(d->B, d->G, d->H, d->q_n) && egv_attn_fewkeys_bwd(a, d->B, st)) {
+        egv_attn_note_path(41);
         EGV_LAUNCH_CHECK();                      // many queries over <= 32 keys, mask allowed (egv_attn_cross.hip)
         return 0;
     }
     if (!d->extra && d->ws && d->q_n <= 32 && d->ws_bytes >= egv_attn_fewq_workspace_bytes(d->B, d->G, d->H, d->k_n) && egv_attn_fewq_bwd(a, d->B, st)) {
+        egv_attn_note_path(42);
         EGV_LAUNCH_CHECK();                      // <= 32 queries over many keys, dropout allowed (egv_attn_cross.hip)
         return 0;
     }
@@ -871,12 +896,14 @@ extern "C" int egv_attn_bwd_pair_covers_extra(int dtype, const egv_attn_desc* d)
     return egv_attn_bwd_pair_cls_ok(a) ? 1 : 0;
 }
 extern "C" int egv_attn_bwd_extra_reduce(int dtype, const egv_attn_desc* d, int self_term, void* stream) {
+    reset_path();
     if (check_desc(d, "egv_attn_bwd_extra_reduce")) return -1;
     EGV_CHECK(dtype == EGV_BF16 && d->ws && d->extra && d->dQ && d->dK && d->dV && d->lse && d->dO && d->O,
               "egv_attn_bwd_extra_reduce: bf16 launch with workspace, extra row, O, dO, lse and the three gradient tensors");
     EGV_CHECK(d->ws_bytes >= egv_attn_bwd_fused_workspace_bytes(d->B, d->G, d->H), "egv_attn_bwd_extra_reduce: workspace too small");
     AttnArgs a = to_args(d);
     egv_attn_bwd_cls_reduce_launch(a, d->B, self_term, reinterpret_cast<hipStream_t>(stream));
+    egv_attn_note_path(51);
     EGV_LAUNCH_CHECK();
     return 0;
 }
@@ -898,6 +925,7 @@ static void attn_work(int dtype, const egv_attn_desc* d, int kind, double& flops
 #define EGV_ATTN_ENTRY(NAME, KIND)                                                              \
     extern "C" int NAME(int dtype, const egv_attn_desc* d, void* stream) {                      \
         void* ph = egv_prof_begin(stream);                                                      \
+        reset_path();                                                                           \
         const int rc = NAME##_impl(dtype, d, stream);                                           \
         if (ph) {                                                                               \
             double fl = 0, by = 0;                                                              \

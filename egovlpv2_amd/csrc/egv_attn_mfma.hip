@@ -253,12 +253,13 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_mfma_kernel(const AttnArgs a
             if (t & 1) __builtin_amdgcn_sched_barrier(0);
         }
         m = grp_max(m);
+        const float mu = m == -INFINITY ? 0.f : m;    // a split chunk whose keys are all masked: p = 0, not exp2(-inf + inf)
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             if (tile_live<NL>(t, ntot)) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float e = exp2_fast(s[t][r] - m);
+                    const float e = exp2_fast(s[t][r] - mu);
                     s[t][r] = e;
                     l += e;
                 }
@@ -1029,11 +1030,11 @@ int egv_attn_fwd_mfma(const AttnArgs& ain, int B, hipStream_t st) {
     int nw, tpw, chunks;
     own_split(a.q.n, nw, tpw, chunks);
     chunks *= a.nsplit;
-    if (ntot > 224) EGV_MFMA_LAUNCH(attn_fwd_mfma_kernel, fwd_lds, 18, 0);      // 256 patches + CLS (14 x 14 patches of a 224^2 frame)
-    else if (ntot <= 32) EGV_MFMA_LAUNCH(attn_fwd_mfma_kernel, fwd_lds, 2, 0);
-    else if (ntot <= 64) EGV_MFMA_LAUNCH(attn_fwd_mfma_kernel, fwd_lds, 4, 0);
-    else if (ntot > 192 && ntot <= 208 && a.nsplit == 1) { if (cls) ++tpw; EGV_MFMA_LAUNCH(attn_fwd_mfma_kernel, fwd_lds, 14, 13); }     // 196 patches + CLS: 13 live tiles known at compile time (-20 % on the forward; measured slower on the two backward kernels)
-    else { if (cls) ++tpw; EGV_MFMA_LAUNCH(attn_fwd_mfma_kernel, fwd_lds, 14, 0); }
+    if (ntot > 224) { egv_attn_note_variant(18); EGV_MFMA_LAUNCH(attn_fwd_mfma_kernel, fwd_lds, 18, 0); }     // 256 patches + CLS (14 x 14 patches of a 224^2 frame)
+    else if (ntot <= 32) { egv_attn_note_variant(2); EGV_MFMA_LAUNCH(attn_fwd_mfma_kernel, fwd_lds, 2, 0); }
+    else if (ntot <= 64) { egv_attn_note_variant(4); EGV_MFMA_LAUNCH(attn_fwd_mfma_kernel, fwd_lds, 4, 0); }
+    else if (ntot > 192 && ntot <= 208 && a.nsplit == 1) { if (cls) ++tpw; egv_attn_note_variant(13); EGV_MFMA_LAUNCH(attn_fwd_mfma_kernel, fwd_lds, 14, 13); }     // 196 patches + CLS: 13 live tiles known at compile time (-20 % on the forward; measured slower on the two backward kernels)
+    else { if (cls) ++tpw; egv_attn_note_variant(14); EGV_MFMA_LAUNCH(attn_fwd_mfma_kernel, fwd_lds, 14, 0); }
     return cls ? 2 : 1;
 }
 
@@ -1057,9 +1058,11 @@ int egv_attn_dq_mfma(const AttnArgs& ain, int B, hipStream_t st) {
     int nw, tpw, chunks;
     own_split(a.q.n, nw, tpw, chunks);
     chunks *= a.nsplit;
-    if (ntot > 224) EGV_MFMA_LAUNCH(attn_dq_mfma_kernel, dq_lds, 18, 0);
-    else if (ntot <= 32) EGV_MFMA_LAUNCH(attn_dq_mfma_kernel, dq_lds, 2, 0);
-    else if (ntot <= 64) EGV_MFMA_LAUNCH(attn_dq_mfma_kernel, dq_lds, 4, 0);
+    const int nt = ntot > 224 ? 18 : (ntot <= 32 ? 2 : (ntot <= 64 ? 4 : 14));
+    egv_attn_note_variant(nt);
+    if (nt == 18) EGV_MFMA_LAUNCH(attn_dq_mfma_kernel, dq_lds, 18, 0);
+    else if (nt == 2) EGV_MFMA_LAUNCH(attn_dq_mfma_kernel, dq_lds, 2, 0);
+    else if (nt == 4) EGV_MFMA_LAUNCH(attn_dq_mfma_kernel, dq_lds, 4, 0);
     else EGV_MFMA_LAUNCH(attn_dq_mfma_kernel, dq_lds, 14, 0);
     return 1;
 }
@@ -1074,9 +1077,11 @@ int egv_attn_dkv_mfma(const AttnArgs& ain, int B, hipStream_t st) {
     int nw, tpw, chunks;
     own_split(a.k.n, nw, tpw, chunks);
     chunks *= a.nsplit;
-    if (ntot > 224) EGV_MFMA_LAUNCH(attn_dkv_mfma_kernel, dkv_lds, 18, 0);
-    else if (ntot <= 32) EGV_MFMA_LAUNCH(attn_dkv_mfma_kernel, dkv_lds, 2, 0);
-    else if (ntot <= 64) EGV_MFMA_LAUNCH(attn_dkv_mfma_kernel, dkv_lds, 4, 0);
+    const int nt = ntot > 224 ? 18 : (ntot <= 32 ? 2 : (ntot <= 64 ? 4 : 14));
+    egv_attn_note_variant(nt);
+    if (nt == 18) EGV_MFMA_LAUNCH(attn_dkv_mfma_kernel, dkv_lds, 18, 0);
+    else if (nt == 2) EGV_MFMA_LAUNCH(attn_dkv_mfma_kernel, dkv_lds, 2, 0);
+    else if (nt == 4) EGV_MFMA_LAUNCH(attn_dkv_mfma_kernel, dkv_lds, 4, 0);
     else EGV_MFMA_LAUNCH(attn_dkv_mfma_kernel, dkv_lds, 14, 0);
     return 1;
 }
@@ -1089,11 +1094,13 @@ int egv_attn_bwd_fused_mfma(const AttnArgs& a, int B, hipStream_t st) {
     // leaves the CLS row's gradients as per-group partials; the (CLS, CLS) term is added by the reduction
     static const bool time_fused = egv_cfg_on("EGV_ATTN_TIME_FUSED", true);
     if (time_fused && a.q.n <= 16 && a.ws && a.extra && egv_attn_time_bwd(a, B, st)) {
+        egv_attn_note_path(43);
         hipLaunchKernelGGL(attn_cls_reduce_kernel, dim3(B, a.H), dim3(256), 0, st, a, 1);
         return 1;
     }
     // long groups (space attention): two-phase kernel on row-major LDS images (egv_attn_space.hip)
     if (a.delta && a.lse && egv_attn_space_bwd(a, B, st)) {
+        egv_attn_note_path(a.ws && a.extra ? 45 : 44);
         if (a.ws && a.extra) hipLaunchKernelGGL(attn_cls_reduce_kernel, dim3(B, a.H), dim3(256), 0, st, a, 0);
         return 1;
     }
@@ -1102,9 +1109,11 @@ int egv_attn_bwd_fused_mfma(const AttnArgs& a, int B, hipStream_t st) {
     if (!aligned_ok(a) || (a.lddq % 4) || (a.dqoff % 4) || (a.lddk % 4) || (a.lddv % 4) || (a.dkoff % 4) || (a.dvoff % 4)) return 0;
     if (a.mask || a.drop_p > 0.f || a.nsplit > 1 || ntot > 224 || ntot <= 64 || own > 2 * FNW || !a.delta || !a.lse) return 0;
     if (a.ws && a.extra && a.extra_row != 0) return 0;            // partials of the extra row: written for the CLS-first layout only
+    if (a.O32) return 0;                                           // delta from O only: the dQ kernel reads egv_attn_desc::O32
     constexpr size_t lds = fused_lds<14>();
     set_lds(attn_bwd_fused_kernel<14>, lds);
     hipLaunchKernelGGL((attn_bwd_fused_kernel<14>), dim3(1, B * a.G, a.H), dim3(64 * FNW), lds, st, a);
+    egv_attn_note_path(a.ws && a.extra ? 47 : 46);
     if (a.ws && a.extra) hipLaunchKernelGGL(attn_cls_reduce_kernel, dim3(B, a.H), dim3(256), 0, st, a, 0);
     return 1;
 }

@@ -426,6 +426,7 @@ static bool space_args(const AttnArgs& a, int B, bool backward, SpaceArgs& s) {
     const bool same = a.q.bs == a.k.bs && a.q.base == a.k.base && a.q.gs == a.k.gs && a.q.is == a.k.is && a.q.n == a.k.n;
     auto ok8 = [](long long x) { return (x % 8) == 0; };
     if (!(same && a.q.n >= 17 && a.q.n + 1 <= 17 * 16 && a.extra && a.extra_row == 0 && !a.mask && a.drop_p <= 0.f && a.nsplit == 1 && a.O)) return false;
+    if (a.O32) return false;                                       // O only: the MFMA kernels write / read egv_attn_desc::O32
     if (!(ok8(a.ldq) && ok8(a.ldo) && ok8(a.qoff) && ok8(a.koff) && ok8(a.voff) && ok8(a.ooff) && a.ldq == a.ldk && a.ldq == a.ldv)) return false;
     const long long rows = (long long)B * a.extra_bs;
     if (rows * a.ldq * 2 >= (1LL << 31) || rows * a.ldo * 2 >= (1LL << 31)) return false;
@@ -461,6 +462,7 @@ bool egv_attn_space_fwd_ok(const AttnArgs& a, int B) {
 template <int NT, bool EXACT>
 static void launch_space_fwd(const SpaceArgs& s, int nwg, hipStream_t st) {
     constexpr size_t lds = s_fwd_lds<NT>();
+    egv_attn_note_variant(EXACT ? NT : 50 + NT);
     static bool attr = false;
     if (!attr && lds > 64 * 1024) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_space_fwd_kernel<NT, EXACT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -471,6 +473,7 @@ static void launch_space_fwd(const SpaceArgs& s, int nwg, hipStream_t st) {
 template <int NT, bool EXACT>
 static void launch_space_bwd(const SpaceArgs& s, int nwg, hipStream_t st) {
     constexpr size_t lds = s_bwd_lds<NT>();
+    egv_attn_note_variant(EXACT ? NT : 50 + NT);
     static bool attr = false;
     if (!attr && lds > 64 * 1024) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_space_bwd_kernel<NT, EXACT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

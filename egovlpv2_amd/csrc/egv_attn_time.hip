@@ -403,6 +403,7 @@ int egv_attn_time_bwd(const AttnArgs& a, int B, hipStream_t st) {
     const bool same = a.q.bs == a.k.bs && a.q.base == a.k.base && a.q.gs == a.k.gs && a.q.is == a.k.is && a.q.n == a.k.n;
     auto ok8 = [](int x) { return (x % 8) == 0; };
     if (!same || a.q.n > 16 || a.q.n < 1 || !a.extra || a.extra_row != 0 || !a.ws || a.mask || a.drop_p > 0.f || a.nsplit > 1) return 0;
+    if (a.O32) return 0;                                            // writes / reads O only (egv_attn_desc::O32: the pair does)
     if (!a.O || !a.dO || !a.lse || !a.delta || !a.dQ || !a.dK || !a.dV) return 0;
     if (!(ok8(a.ldq) && ok8(a.ldk) && ok8(a.ldv) && ok8(a.ldo) && ok8(a.qoff) && ok8(a.koff) && ok8(a.voff) && ok8(a.ooff))) return 0;
     if ((a.lddq % 4) || (a.lddk % 4) || (a.lddv % 4) || (a.dqoff % 4) || (a.dkoff % 4) || (a.dvoff % 4)) return 0;
@@ -420,7 +421,7 @@ int egv_attn_time_bwd(const AttnArgs& a, int B, hipStream_t st) {
 static bool time_fwd_shape_ok(const AttnArgs& a) {
     const bool same = a.q.bs == a.k.bs && a.q.base == a.k.base && a.q.gs == a.k.gs && a.q.is == a.k.is && a.q.n == a.k.n;
     auto ok8 = [](int x) { return (x % 8) == 0; };
-    return same && a.q.n <= 16 && a.q.n >= 1 && a.extra && a.extra_row == 0 && a.ws && !a.mask && a.drop_p <= 0.f && a.nsplit == 1 && a.O &&
+    return same && a.q.n <= 16 && a.q.n >= 1 && a.extra && a.extra_row == 0 && a.ws && !a.mask && a.drop_p <= 0.f && a.nsplit == 1 && a.O && !a.O32 &&
            ok8(a.ldq) && ok8(a.ldk) && ok8(a.ldv) && ok8(a.ldo) && ok8(a.qoff) && ok8(a.koff) && ok8(a.voff) && ok8(a.ooff) && a.ldq == a.ldk &&
            a.ldq == a.ldv;
 }

@@ -2022,6 +2022,11 @@ def egonce(x, sim_v, sim_n, temperature=0.05, noun=True, verb=True):
     return EgoNCEFn.apply(x, sim_v, sim_n, temperature, noun, verb)
 
 
+def attn_last_path() -> int:
+    """kind * 100 + tile instance of the kernel path the last attention entry call on this thread enqueued (0: none)"""
+    return lib.egv_attn_last_path()
+
+
 # ---- GEMM instrumentation (bench.py roofline) -------------------------------------------------------------
 def prof_enable(on: bool):
     lib.egv_prof_enable(1 if on else 0)

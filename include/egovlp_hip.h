@@ -174,8 +174,9 @@ typedef struct egv_attn_desc {
     int nsplit; float* ws; long long ws_bytes;   /* split of the other-side loop, fp32 partial slabs */
     float drop_p; unsigned int drop_seed;        /* attention-probability dropout (roberta.py:313): P~ = P * keep/(1-p); the mask is a
                                                     counter-based function of (seed, query row, key row, head); 0 = off */
-    float* O32;                                  /* optional (bf16 storage): fp32 values of O, [rows, ldo] with the offsets of O.  egv_attn_fwd
-                                                    writes it (split form and the unsplit MFMA kernel), egv_attn_bwd_dq forms
+    float* O32;                                  /* optional (bf16 storage): fp32 values of O, [rows, ldo] with the offsets of O.  Every
+                                                    egv_attn_fwd path writes it (the kernels that cannot -- time, space and many-queries-
+                                                    over-few-keys -- decline a launch that sets it), egv_attn_bwd_dq forms
                                                     delta = rowsum(dO o O) from it.  A query over thousands of keys (text -> image) has nearly
                                                     uniform probabilities: dS = P o (dP - delta) is a small difference and the bf16 rounding of
                                                     O puts a COMMON offset into delta -- 3-5 x the q / k gradient error of the reference
@@ -218,6 +219,9 @@ long long egv_attn_fewq_workspace_bytes(int B, int G, int H, int k_n);
  * extra-key term, which no group owns) -- the one-query / one-key launches of the CLS row are not needed. */
 int egv_attn_bwd_pair_covers_extra(int dtype, const egv_attn_desc* d);
 int egv_attn_bwd_extra_reduce(int dtype, const egv_attn_desc* d, int self_term, void* stream);
+/* The kernel path the last attention entry call (egv_attn_fwd, _bwd_dq, _bwd_dkv, _bwd_fused, _bwd_extra_reduce) on the calling
+ * thread enqueued: kind * 100 + tile instance, 0 when it enqueued nothing.  The numbering is listed in tests/test_attention_paths.py. */
+int egv_attn_last_path(void);
 
 /* ---- patch embedding pre/post (video_transformer.py:78-83,356-371; model.py:212-231,296-317) ---- */
 int egv_im2col(int dtype, const float* video, void* out, int BF, int C, int H, int W, int P, void* stream);
